@@ -87,6 +87,38 @@ def gen_data(ctx, rows, cols, classes, dtype, sparsity=0.9, seed=7):
     return X1, y1, X2, y2
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, outputs, write=True):
+    """Write the arrays a step returned as path/<name>.npy (float32, or float64 for fp64 runs).
+    Every rank converts (a row-partitioned result is gathered, which is a collective); `write`
+    selects the rank that stores the files.  The outputs of this benchmark are D x 1 and
+    D x (k-1) coefficient matrices; should they ever exceed DUMP_MAX_BYTES in all, a fixed
+    seeded sample of each array's cells is stored instead."""
+    import numpy as np
+    from systemml_amd.parallel import dist as D
+    arrs = {}
+    for name, v in outputs.items():
+        if isinstance(v, D.DistMatrix):
+            v = D.gather(v)
+        if hasattr(v, "to_matrix"):
+            v = v.to_matrix()
+        t = v.detach() if hasattr(v, "detach") else torch.as_tensor(v)
+        t = t.to_dense() if t.layout != torch.strided else t
+        t = t.cpu()
+        arrs[name] = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).numpy()
+    if not write:
+        return
+    budget = DUMP_MAX_BYTES // max(1, len(arrs))
+    os.makedirs(path, exist_ok=True)
+    for name, x in arrs.items():
+        if x.nbytes > budget:
+            idx = np.random.default_rng(0).choice(x.size, budget // x.itemsize, replace=False)
+            x = x.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(path, name + ".npy"), x)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -120,7 +152,16 @@ def main():
     ap.add_argument("--compiler", default="process", choices=["process", "thread"],
                     help="where the next step's scripts compile while this step executes: a compiler "
                          "process (api/compile_service.py, off the executor's interpreter lock) or a thread")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (the B_out of "
+                         "LinearRegCG and of MultiLogReg) to DIR/<name>.npy; the inputs are seeded, so two "
+                         "builds run with the same arguments can be compared output for output")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements and checks beyond the headline figure (there are none "
+                         "in this benchmark today: a plain run already times only the steps)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # the compiler service is started before anything touches the GPU (its process is spawned)
     svc = None
@@ -230,6 +271,7 @@ def main():
         return r1["B_out"], r2["B_out"], (nxt.result() if nxt is not None else None)
 
     fixed = compile_both() if a.reuse_plans else None
+    last = {}     # what the most recent step returned (--dump-outputs)
 
     def run_steps(k, stats=None, cs=None):
         # every step compiles the scripts of the step after it while it executes (the last
@@ -237,7 +279,8 @@ def main():
         # before the clock stops): each timed step carries one compilation of both scripts
         cs = fixed if fixed is not None else cs
         for i in range(k):
-            _, _, cs = step(stats, cs, prefetch_next=fixed is None and not a.no_overlap)
+            last["linreg_B_out"], last["mlogreg_B_out"], cs = step(
+                stats, cs, prefetch_next=fixed is None and not a.no_overlap)
             cs = fixed if fixed is not None else cs
         return cs
 
@@ -289,6 +332,8 @@ def main():
         if rank == 0 and a.verbose:
             print(f"collectives per step: { {k: v / max(1, a.steps + a.warmup) for k, v in D.stats.items()} }",
                   file=sys.stderr)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, last, write=rank == 0)
     if prof is not None and rank == 0:
         import io
         import pstats

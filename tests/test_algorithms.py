@@ -108,10 +108,10 @@ def test_kmeans_finds_separated_clusters():
         assert np.min(np.linalg.norm(C - c, axis=1)) < 0.5
 
 
-def test_pca_eigenvalues():
+def test_pca_eigenvalues(tmp_path):
     rng = np.random.default_rng(6)
     A = rng.standard_normal((200, 5)) @ rng.standard_normal((5, 5))
-    r, _ = algo("PCA", dict(INPUT="A", K=2, CENTER=1, OUTPUT="/tmp/_pca_test", PROJDATA=0), {"A": A}, ["lam"])
+    r, _ = algo("PCA", dict(INPUT="A", K=2, CENTER=1, OUTPUT=str(tmp_path / "_pca_test"), PROJDATA=0), {"A": A}, ["lam"])
     w = np.sort(np.linalg.eigvalsh(np.cov(A.T)))[::-1]
     np.testing.assert_allclose(r["lam"].ravel(), w[:2], rtol=1e-10)
 
@@ -215,13 +215,13 @@ def test_glm_predict_means_and_r2():
     np.testing.assert_allclose(stats["PEARSON_X2"], np.sum((y - mu) ** 2 / mu), rtol=1e-10)
 
 
-def test_univar_stats():
+def test_univar_stats(tmp_path):
     rng = np.random.default_rng(8)
     n = 501
     X = np.hstack([rng.gamma(2.0, 1.5, (n, 1)), rng.integers(1, 5, (n, 1)).astype(float),
                    rng.standard_normal((n, 1)) * 3 + 1, rng.integers(1, 3, (n, 1)).astype(float)])
     types = np.array([[1, 2, 1, 3]], dtype=float)
-    r, _ = algo("Univar-Stats", dict(X="X", TYPES="T", STATS="/tmp/_univar_stats"), {"X": X, "K": types}, ["S"])
+    r, _ = algo("Univar-Stats", dict(X="X", TYPES="T", STATS=str(tmp_path / "_univar_stats")), {"X": X, "K": types}, ["S"])
     S = r["S"]
     for j in (0, 2):
         x = X[:, j]

@@ -3,7 +3,7 @@ TransformFrameEncodeApplyTest, TransformFrameEncodeDecodeTest, TransformFrameEnc
 TransformFrameEncodeApplySubsetTest; data: src/test/scripts/functions/transform/input/homes3).
 
 The reference compares encode vs apply outputs and decode(encode(F)) vs F; we do the same
-on the reference's own homes3 data (read from the reference tree as plain CSV) and on
+on the reference's own homes3 data (stored under tests/golden/homes3 as plain CSV) and on
 synthetic frames with missing values for impute/omit/bin, checked against numpy.
 """
 import os
@@ -19,8 +19,10 @@ from systemml_amd.runtime import transform as T
 
 CFG = DMLConfig(gpu=False)
 REF = "/root/reference/src/test/scripts/functions/transform"
-HOMES = os.path.join(REF, "input", "homes3")
-needs_ref = pytest.mark.skipif(not os.path.isdir(HOMES), reason="reference transform inputs not present")
+# the homes3 inputs (CSV, its metadata and the JSON transform specs) are stored with the tests
+HOMES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "homes3")
+# the two tests that run the reference's own DML scripts need its tree (scripts are not copied)
+needs_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="reference transform scripts not present")
 
 SPECS = ["recode", "recode2", "dummy", "dummy2", "bin", "bin2", "impute", "impute2", "omit", "omit2",
          "recode_dummy", "recode_dummy2", "colmap1", "colmap2"]
@@ -38,7 +40,6 @@ def _run(src, outputs=None, **args):
     return run(src, args=args, outputs=outputs or [], config=CFG)
 
 
-@needs_ref
 @pytest.mark.parametrize("spec", SPECS)
 def test_encode_equals_apply(homes, spec):
     r = _run('''
@@ -59,7 +60,6 @@ X2 = transformapply(target=F1, spec=jspec, meta=M);
         assert X.shape[1] == width
 
 
-@needs_ref
 @pytest.mark.parametrize("spec", ["recode", "recode2", "dummy", "dummy2", "recode_dummy"])
 def test_encode_decode_roundtrip(homes, spec):
     r = _run('''
@@ -176,7 +176,6 @@ G = transformdecode(target=X, spec="{ids: true, recode: [1]}", meta=M)
     assert G.columns[1] == [7.0, 9.0]
 
 
-@needs_ref
 def test_legacy_transform_and_apply_scripts(homes, tmp_path):
     from systemml_amd.api.mlcontext import SCRIPTS_DIR
     spec = os.path.join(HOMES, "homes.tfspec_recode_dummy.json")
