@@ -23,6 +23,13 @@ bytes -- the GPU form of the reference's per-group kernels:
                                                     entries' tuple ids
 * sum / rowSums / colSums operate on dictionaries, tuple counts and entry lists.
 
+The DDC groups with uint8 codes of a matrix in HBM are packed into one row-major code block
+(CLAPack, built on first use) and their X %*% V, t(X) %*% Y (K <= 8) and single-column
+mmchains run on ops/hip/cla.hip: one pass over the codes for all groups instead of one pass
+over the output per group (reference: ColGroupDDC1.rightMultByVector over a group array,
+CompressedMatrixBlock.chainMatrixMultOperations).  The other groups keep the per-group code
+below and are added to the kernels' results; so do all host matrices.
+
 Planning (cocode): per-column distinct counts on a sample, columns with few distinct values
 are greedily merged while the joint tuple count stays <= 255 (uint8 codes).
 """
@@ -96,16 +103,133 @@ class ColGroup:
         return ColGroup(self.kind, self.cols, d, self.nrows, self.codes, self.rows, self.tid, self.starts, self.lens)
 
 
+class CLAPack:
+    """The uint8 DDC groups of one matrix in the layout of ops/hip/cla.hip.
+
+    codes   uint8 n x Gp row-major, Gp = 16 * ceil(G / 16); padding columns hold code 0.
+    toff    int32 [Gp]: row of each group's tuple 0 in the concatenated table of T = sum T_g
+            rows plus the extra row T, which every padding column points at.
+    dvals   all dictionaries, flattened row-major, in the matrix dtype.
+    tup_*   per tuple (T): offset of its values in dvals, its group's column count and the
+            offset of its group's columns in colidx -- the dictionary product P = D V is one
+            launch over the tuples.
+    col_*   per packed column (C): its matrix column, the offset of its first value in dvals,
+            the value stride (column count), and its group's first tuple / tuple count -- the
+            transposed dictionary product is one launch over the columns.
+    valid   every code is below its group's tuple count (checked once, here)."""
+    __slots__ = ("codes", "toff", "toff_host", "G", "Gp", "T", "index", "dvals", "tup_off", "tup_nc", "tup_c0",
+                 "colidx", "col_out", "col_doff", "col_nc", "col_t0", "col_T", "C", "valid", "_chunks")
+
+    def with_dicts(self, groups):
+        """The pack of a matrix with the same codes and other dictionary values (scale)."""
+        p = CLAPack()
+        for a in self.__slots__:
+            setattr(p, a, getattr(self, a))
+        p._chunks = {}
+        p.dvals = torch.cat([groups[i].dict.reshape(-1) for i in self.index])
+        return p
+
+
+def _packable(g):
+    return g.kind == "ddc" and g.codes is not None and g.codes.dtype == torch.uint8
+
+
+def _build_pack(cm):
+    """Pack the uint8 DDC groups of `cm` (plain tensor code: any device) and rebind their codes
+    to column views of the packed block; None when no group qualifies."""
+    index = [i for i, g in enumerate(cm.groups) if _packable(g)]
+    if not index:
+        return None
+    gs = [cm.groups[i] for i in index]
+    n, dev = cm.shape[0], cm.device
+    G = len(gs)
+    Gp = 16 * ((G + 15) // 16)
+    p = CLAPack()
+    p.G, p.Gp, p.index, p._chunks = G, Gp, index, {}
+    Ts = [int(g.dict.shape[0]) for g in gs]
+    ncs = [int(g.cols.numel()) for g in gs]
+    T = sum(Ts)
+    toff = [0] * G
+    for j in range(1, G):
+        toff[j] = toff[j - 1] + Ts[j - 1]
+    p.T = T
+    p.toff_host = toff + [T] * (Gp - G)
+    i32 = dict(dtype=torch.int32, device=dev)
+    p.toff = torch.tensor(p.toff_host, **i32)
+    codes = torch.zeros((n, Gp), dtype=torch.uint8, device=dev)
+    if n > 0:
+        codes[:, :G] = torch.stack([g.codes for g in gs], dim=1)
+    # one reduction and one host read: the kernels index LDS tables by these codes
+    p.valid = n == 0 or bool((codes[:, :G].amax(0).to(torch.int32) < torch.tensor(Ts, **i32)).all().item())
+    p.codes = codes
+    for j, g in enumerate(gs):
+        g.codes = codes[:, j]
+    p.dvals = torch.cat([g.dict.reshape(-1) for g in gs])
+    doff, coff = [0] * G, [0] * G
+    for j in range(1, G):
+        doff[j] = doff[j - 1] + Ts[j - 1] * ncs[j - 1]
+        coff[j] = coff[j - 1] + ncs[j - 1]
+    tid = torch.arange(T, **i32)
+    grp = torch.repeat_interleave(torch.arange(G, device=dev), torch.tensor(Ts, device=dev))
+    t_nc = torch.tensor(ncs, **i32)[grp]
+    p.tup_nc = t_nc
+    p.tup_off = torch.tensor(doff, **i32)[grp] + (tid - p.toff[:G][grp]) * t_nc
+    p.tup_c0 = torch.tensor(coff, **i32)[grp]
+    p.colidx = torch.cat([g.cols for g in gs]).to(torch.int32)
+    p.C = int(p.colidx.numel())
+    cgrp = torch.repeat_interleave(torch.arange(G, device=dev), torch.tensor(ncs, device=dev))
+    p.col_out = p.colidx
+    p.col_nc = torch.tensor(ncs, **i32)[cgrp]
+    p.col_doff = torch.tensor(doff, **i32)[cgrp] + (torch.arange(p.C, **i32) - torch.tensor(coff, **i32)[cgrp])
+    p.col_t0 = p.toff[:G][cgrp]
+    p.col_T = torch.tensor(Ts, **i32)[cgrp]
+    return p
+
+
 class CompressedMatrix:
     def __init__(self, nrows, ncols, groups, dtype, device):
         self.shape = (nrows, ncols)
         self.groups = groups
         self.dtype = dtype
         self.device = device
+        self._pack = False            # False: not built yet; None: no uint8 DDC group
+
+    # ------------------------------------------------------------------ packed DDC block
+    def pack(self):
+        """The packed uint8 DDC groups (CLAPack), built on first use and kept; None for host
+        matrices and when no group qualifies."""
+        if self._pack is False:
+            if torch.device(self.device).type != "cuda":
+                return None
+            self._pack = _build_pack(self)
+        return self._pack
+
+    def _cla_on(self):
+        """The HIP kernels of ops/hip/cla.hip serve this matrix (HBM, fp32 / fp64, kernels on)."""
+        if torch.device(self.device).type != "cuda" or self.dtype not in (torch.float32, torch.float64):
+            return False
+        from .backend import backend
+        from . import kernels
+        return bool(backend.use_kernels and kernels.CLA)
+
+    def _cla(self, K):
+        """The pack when a product with K columns runs on the HIP kernels."""
+        if K < 1 or K > 8 or not self._cla_on():
+            return None
+        p = self.pack()
+        return p if p is not None and p.valid else None
+
+    def _rest(self, p):
+        packed = set(p.index)
+        return [g for i, g in enumerate(self.groups) if i not in packed]
 
     # ------------------------------------------------------------------ info
     def nbytes(self):
-        return sum(g.nbytes() for g in self.groups)
+        b = sum(g.nbytes() for g in self.groups)
+        p = self._pack
+        if p:
+            b += self.shape[0] * (p.Gp - p.G)      # the padding columns of the packed codes
+        return b
 
     def ratio(self):
         return self.shape[0] * self.shape[1] * torch.empty((), dtype=self.dtype).element_size() / max(self.nbytes(), 1)
@@ -139,8 +263,18 @@ class CompressedMatrix:
     def matmul(self, V):
         """X %*% V."""
         V = V.to(self.dtype)
+        p = self._cla(V.shape[1]) if V.dim() == 2 else None
+        if p is not None:
+            from . import kernels
+            rest = self._rest(p)
+            r = kernels.cla_rmm(p, V, self._matmul_groups(rest, V) if rest else None)
+            if r is not None:
+                return r
+        return self._matmul_groups(self.groups, V)
+
+    def _matmul_groups(self, groups, V):
         out = torch.zeros((self.shape[0], V.shape[1]), dtype=self.dtype, device=self.device)
-        for g in self.groups:
+        for g in groups:
             Vg = V.index_select(0, g.cols)
             if g.kind == "unc":
                 out += g.dict @ Vg
@@ -155,7 +289,15 @@ class CompressedMatrix:
         """t(X) %*% Y."""
         Y = Y.to(self.dtype)
         out = torch.zeros((self.shape[1], Y.shape[1]), dtype=self.dtype, device=self.device)
-        for g in self.groups:
+        p = self._cla(Y.shape[1]) if Y.dim() == 2 else None
+        if p is not None:
+            from . import kernels
+            if kernels.cla_lmm(p, Y, out) is not None:
+                return self._tmatmul_groups(self._rest(p), Y, out)
+        return self._tmatmul_groups(self.groups, Y, out)
+
+    def _tmatmul_groups(self, groups, Y, out):
+        for g in groups:
             if g.kind == "unc":
                 out[g.cols] = g.dict.t() @ Y
                 continue
@@ -167,6 +309,27 @@ class CompressedMatrix:
                 bins.index_add_(0, tid, Y.index_select(0, rows))
             out[g.cols] = g.dict.t() @ bins
         return out
+
+    def mmchain(self, ctype, v, w=None):
+        """t(X) %*% f(X %*% v) for a single column v on the one-pass HIP chain (XtXv: f = id,
+        XtwXv: w * u, XtXvy: u - y); None when it does not apply (host matrices, no packed
+        group, other chain types, K > 1) and the caller composes the two products."""
+        if ctype not in ("XtXv", "XtwXv", "XtXvy") or v.dim() != 2 or v.shape[1] != 1 or v.shape[0] != self.shape[1]:
+            return None
+        if (w is None) != (ctype == "XtXv") or (w is not None and tuple(w.shape) != (self.shape[0], 1)):
+            return None
+        p = self._cla(1)
+        if p is None:
+            return None
+        from . import kernels
+        v = v.to(device=self.device, dtype=self.dtype)
+        w = w.to(device=self.device, dtype=self.dtype) if w is not None else None
+        rest = self._rest(p)
+        out = torch.zeros((self.shape[1], 1), dtype=self.dtype, device=self.device)
+        g = kernels.cla_chain(p, ctype, v, w, self._matmul_groups(rest, v) if rest else None, out, bool(rest))
+        if g is None:
+            return None
+        return self._tmatmul_groups(rest, g, out) if rest else out
 
     # ------------------------------------------------------------------ aggregates
     def colsums(self, sq=False):
@@ -198,8 +361,13 @@ class CompressedMatrix:
         factor (0 * inf = NaN) is applied to the decompressed matrix instead."""
         if not math.isfinite(s) and any(g.kind in ("ole", "rle") for g in self.groups):
             return self.decompress() * s
+        if self._cla_on():
+            self.pack()               # before the groups are copied: they share the packed codes
         gs = [g.with_dict(g.dict * s) for g in self.groups]
-        return CompressedMatrix(self.shape[0], self.shape[1], gs, self.dtype, self.device)
+        cm = CompressedMatrix(self.shape[0], self.shape[1], gs, self.dtype, self.device)
+        if self._pack is not False:   # same codes and offsets, new dictionary values
+            cm._pack = self._pack.with_dicts(gs) if self._pack is not None else None
+        return cm
 
 
 def is_compressed(x):

@@ -769,6 +769,11 @@ def mmchain(ctype, X, v, w=None):
         r = kernels.try_mmchain(ctype, X, v, w)
         if r is not None:
             return r
+    if CMP.is_compressed(X) and isinstance(v, Tensor) and not SP.is_sparse(v) and v.dim() == 2 \
+            and (w is None or (isinstance(w, Tensor) and not SP.is_sparse(w) and w.dim() == 2)):
+        r = X.mmchain(ctype, v, w)        # one pass over the packed DDC codes (ops/hip/cla.hip)
+        if r is not None:
+            return r
     return mmchain_ref(ctype, X, v, w)
 
 

@@ -220,6 +220,24 @@ def load(required=False):
     L.sysml_commit_live.argtypes = [CI, VP, VP, VP, VP, VP]
     L.sysml_perm_compose.restype = CI
     L.sysml_perm_compose.argtypes = [VP, VP, VP, VP, CI, I64, VP]
+    L.sysml_cla_budget.restype = CI
+    L.sysml_cla_budget.argtypes = []
+    L.sysml_cla_set_budget.restype = None
+    L.sysml_cla_set_budget.argtypes = [CI]
+    L.sysml_cla_dictmm.restype = CI
+    L.sysml_cla_dictmm.argtypes = [CI] + [VP] * 6 + [CI, CI, CI, VP, VP]
+    L.sysml_cla_threads.restype = CI
+    L.sysml_cla_threads.argtypes = []
+    L.sysml_cla_fold.restype = CI
+    L.sysml_cla_fold.argtypes = [VP, VP, CI, I64, VP]
+    L.sysml_cla_dicttmm.restype = CI
+    L.sysml_cla_dicttmm.argtypes = [CI] + [VP] * 6 + [CI, VP, CI, CI, VP, CI, VP]
+    L.sysml_cla_rmm.restype = CI
+    L.sysml_cla_rmm.argtypes = [CI, VP, I64, CI, VP, VP, CI, CI, CI, VP, CI, VP, CI, CI, VP, CI, VP]
+    L.sysml_cla_lmm.restype = CI
+    L.sysml_cla_lmm.argtypes = [CI, VP, I64, CI, VP, CI, VP, CI, CI, CI, CI, I64, VP, CI, VP]
+    L.sysml_cla_chain.restype = CI
+    L.sysml_cla_chain.argtypes = [CI, VP, I64, CI, VP, VP, CI, VP, VP, CI, VP, VP, CI, VP]
     _lib = L
     return L
 
@@ -1966,3 +1984,205 @@ def live_and(prev_enc, q_enc):
     if rc != 0:
         raise RuntimeError(f"sysml_live_and failed: {rc}")
     return out
+
+
+# ----------------------------------------------------------------------------
+# Compressed linear algebra on packed uint8 DDC groups (ops/hip/cla.hip; the layout is
+# ops/compress.CLAPack).  SYSML_CLA=0 keeps the per-group torch operators (A/B switch).
+# ----------------------------------------------------------------------------
+CLA = os.environ.get("SYSML_CLA", "1") != "0"
+_CLA_LDS_MAX = 160 * 1024        # LDS of one CU
+_CLA_SLAB_MAX = 256 << 20        # bytes of per-block fp64 bins one product may write
+_CLA_BPC = 8                     # workgroups per CU at most (each writes a row of the slab)
+_CLA_EPI = {"XtXv": 0, "XtwXv": 1, "XtXvy": 2}
+_cla_cu = {}
+
+
+def _cla_dt(dtype):
+    return 1 if dtype == torch.float32 else 2 if dtype == torch.float64 else None
+
+
+def _cla_cus(device):
+    i = torch.device(device).index or 0
+    if i not in _cla_cu:
+        _cla_cu[i] = torch.cuda.get_device_properties(i).multi_processor_count
+    return _cla_cu[i]
+
+
+def _cla_rows(x, dtype):
+    """x as a row-major view of the matrix dtype and its leading dimension."""
+    x = x.to(dtype)
+    if x.stride(1) != 1 or x.stride(0) < x.shape[1]:
+        x = x.contiguous()
+    return x, x.stride(0)
+
+
+def _cla_table(L, p, V, kp):
+    """P = D %*% V[cols] for every tuple of every packed group: (T + 1) x kp, row T zero."""
+    V = V.contiguous()
+    P = torch.empty((p.T + 1, kp), dtype=V.dtype, device=V.device)
+    rc = L.sysml_cla_dictmm(_cla_dt(V.dtype), p.dvals.data_ptr(), p.tup_off.data_ptr(), p.tup_nc.data_ptr(),
+                            p.tup_c0.data_ptr(), p.colidx.data_ptr(), V.data_ptr(), V.shape[1], kp, p.T, P.data_ptr(),
+                            _stream())
+    if rc != 0:
+        raise RuntimeError(f"sysml_cla_dictmm failed: {rc}")
+    return P
+
+
+def _cla_chunks(L, p, kp):
+    """(groups per chunk, LDS bytes of the largest chunk) such that the fp64 bins of every chunk of
+    consecutive groups fit the LDS budget: whole 16-group code vectors, or a part (8, 4, 2, 1
+    groups) of one when 16 groups do not fit; None when one group's bins do not."""
+    budget = L.sysml_cla_budget()
+    key = (kp, budget)
+    if key in p._chunks:
+        return p._chunks[key]
+    bound = lambda g: p.toff_host[g] if g < p.Gp else p.T
+    res = None
+    for gpc in list(range(p.Gp, 0, -16)) + [8, 4, 2, 1]:
+        worst = max(bound(g + gpc) - bound(g) for g in range(0, p.Gp, gpc))
+        if worst * kp * 8 <= budget:
+            lds = max(worst * kp * 8 + min(gpc, p.Gp) * 4, 16)
+            res = (gpc, lds) if lds <= _CLA_LDS_MAX else None
+            break
+    p._chunks[key] = res
+    return res
+
+
+def _cla_grid(p, n, lds, slab_row_bytes=0):
+    """Workgroups of a pass over the codes: what the CUs hold at `lds` bytes each.  The binning
+    kernels (slab_row_bytes > 0) run larger workgroups, and each writes one row of the slab."""
+    per_cu = max(1, min(_CLA_BPC, _CLA_LDS_MAX // max(lds, 1)))
+    threads = 256
+    if slab_row_bytes:
+        threads = load().sysml_cla_threads()
+        per_cu = max(1, min(per_cu, 2048 // threads))
+    grid = min(_cla_cus(p.codes.device) * per_cu, (n + threads - 1) // threads)
+    if slab_row_bytes:
+        grid = min(grid, _CLA_SLAB_MAX // slab_row_bytes)
+    return max(grid, 1)
+
+
+def _cla_gather(L, p, P, K, kp, u0, epi=0, w=None):
+    n = p.codes.shape[0]
+    out = torch.empty((n, K), dtype=P.dtype, device=P.device)
+    ldu = 0
+    if u0 is not None:
+        u0, ldu = _cla_rows(u0, P.dtype)
+    es = P.element_size()
+    tab = (p.T + 1) * kp * es
+    lds = p.Gp * 4 + (tab if tab <= L.sysml_cla_budget() and p.Gp * 4 + tab <= _CLA_LDS_MAX else 0)
+    rc = L.sysml_cla_rmm(_cla_dt(P.dtype), p.codes.data_ptr(), n, p.Gp, p.toff.data_ptr(), P.data_ptr(), p.T, K, kp,
+                         u0.data_ptr() if u0 is not None else None, ldu, out.data_ptr(), K, epi,
+                         w.data_ptr() if w is not None else None, _cla_grid(p, n, lds) * 4, _stream())
+    if rc != 0:
+        raise RuntimeError(f"sysml_cla_rmm failed: {rc}")
+    return out
+
+
+def _cla_bin(L, p, Y, K, kp, chunks, out):
+    """out[cols of the packed groups, :] = t(X_packed) %*% Y."""
+    n = p.codes.shape[0]
+    Y, ldy = _cla_rows(Y, out.dtype)
+    gpc, lds = chunks
+    width = p.T * kp
+    grid = _cla_grid(p, n, lds, width * 8)
+    slab = torch.empty((grid, width), dtype=torch.float64, device=out.device)
+    rc = L.sysml_cla_lmm(_cla_dt(out.dtype), p.codes.data_ptr(), n, p.Gp, p.toff.data_ptr(), p.T, Y.data_ptr(), ldy,
+                         K, kp, gpc, lds, slab.data_ptr(), grid, _stream())
+    if rc != 0:
+        raise RuntimeError(f"sysml_cla_lmm failed: {rc}")
+    _cla_fold(L, p, slab, K, kp, out)
+
+
+def _cla_fold(L, p, slab, K, kp, out):
+    """Per-block bins -> fixed-order sum -> transposed dictionary product into out's rows."""
+    bins = torch.empty(slab.shape[1], dtype=torch.float64, device=slab.device)
+    rc = L.sysml_cla_fold(slab.data_ptr(), bins.data_ptr(), slab.shape[0], slab.shape[1], _stream())
+    if rc != 0:
+        raise RuntimeError(f"sysml_cla_fold failed: {rc}")
+    rc = L.sysml_cla_dicttmm(_cla_dt(out.dtype), p.dvals.data_ptr(), p.col_out.data_ptr(), p.col_doff.data_ptr(),
+                             p.col_nc.data_ptr(), p.col_t0.data_ptr(), p.col_T.data_ptr(), p.C, bins.data_ptr(), K, kp,
+                             out.data_ptr(), out.stride(0), _stream())
+    if rc != 0:
+        raise RuntimeError(f"sysml_cla_dicttmm failed: {rc}")
+
+
+def _cla_ok(p, *tensors):
+    if not CLA or p is None or not p.valid or not p.codes.is_cuda or p.codes.shape[0] < 1 or p.Gp > 16384:
+        return False
+    dt = p.dvals.dtype
+    return _cla_dt(dt) is not None and all(t is None or (t.is_cuda and t.dtype == dt and t.dim() == 2) for t in tensors)
+
+
+def cla_rmm(p, V, u0=None):
+    """X_packed %*% V + u0 for the packed uint8 DDC groups of a compressed matrix (V: D x K in
+    the matrix dtype, K <= 8; u0: N x K, the product of the matrix's other groups): one dictionary
+    product and one pass over the codes.  None when not applicable."""
+    if not _cla_ok(p, V, u0) or not 1 <= V.shape[1] <= 8:
+        return None
+    L = load(required=True)
+    K = V.shape[1]
+    kp = _kpad(K)
+    out = _cla_gather(L, p, _cla_table(L, p, V, kp), K, kp, u0)
+    _count("cla.rmm")
+    return out
+
+
+def cla_lmm(p, Y, out):
+    """out[packed columns, :] = t(X_packed) %*% Y (Y: N x K, K <= 8; out: D x K contiguous, its
+    other rows are left alone): fp64 LDS bins per workgroup, summed in a fixed order, then one
+    transposed dictionary product.  None (out untouched) when not applicable."""
+    if not _cla_ok(p, Y, out) or not 1 <= Y.shape[1] <= 8 or Y.shape[0] != p.codes.shape[0] or not out.is_contiguous():
+        return None
+    L = load(required=True)
+    K = Y.shape[1]
+    kp = _kpad(K)
+    chunks = _cla_chunks(L, p, kp)
+    if chunks is None:
+        return None
+    _cla_bin(L, p, Y, K, kp, chunks, out)
+    _count("cla.lmm")
+    return out
+
+
+def cla_chain(p, ctype, v, w, u0, out, want_g=False):
+    """out[packed columns] = t(X_packed) %*% g with g = f(X_packed %*% v + u0, w) for one column
+    v (XtXv: g = u, XtwXv: w * u, XtXvy: u - w).  One pass over the codes when the product table
+    and the fp64 bins fit the LDS budget together (counter cla.chain), else the gather with the
+    row function followed by the binning pass (cla.chain2).  Returns g (N x 1) when want_g, else
+    True; None when not applicable."""
+    if ctype not in _CLA_EPI or not _cla_ok(p, v, w, u0, out) or v.shape[1] != 1 or not out.is_contiguous():
+        return None
+    L = load(required=True)
+    n = p.codes.shape[0]
+    epi = _CLA_EPI[ctype]
+    if (w is None) != (epi == 0) or (w is not None and (w.shape != (n, 1) or not w.is_contiguous())):
+        return None
+    es = v.element_size()
+    tab = p.T * 8 + (p.T + 1) * es
+    fused = tab <= L.sysml_cla_budget() and p.Gp <= 1024
+    chunks = None
+    if not fused:
+        chunks = _cla_chunks(L, p, 1)
+        if chunks is None:
+            return None
+    P = _cla_table(L, p, v, 1)
+    if not fused:
+        g = _cla_gather(L, p, P, 1, 1, u0, epi, w)
+        _cla_bin(L, p, g, 1, 1, chunks, out)
+        _count("cla.chain2")
+        return g if want_g else True
+    if u0 is not None:
+        u0 = u0.contiguous()
+    g = torch.empty((n, 1), dtype=v.dtype, device=v.device) if want_g else None
+    grid = _cla_grid(p, n, tab + p.Gp * 4, p.T * 8)
+    slab = torch.empty((grid, p.T), dtype=torch.float64, device=v.device)
+    rc = L.sysml_cla_chain(_cla_dt(v.dtype), p.codes.data_ptr(), n, p.Gp, p.toff.data_ptr(), P.data_ptr(), p.T,
+                           u0.data_ptr() if u0 is not None else None, w.data_ptr() if w is not None else None, epi,
+                           g.data_ptr() if g is not None else None, slab.data_ptr(), grid, _stream())
+    if rc != 0:
+        raise RuntimeError(f"sysml_cla_chain failed: {rc}")
+    _cla_fold(L, p, slab, 1, 1, out)
+    _count("cla.chain")
+    return g if want_g else True
