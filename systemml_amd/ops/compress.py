@@ -30,6 +30,12 @@ over the output per group (reference: ColGroupDDC1.rightMultByVector over a grou
 CompressedMatrixBlock.chainMatrixMultOperations).  The other groups keep the per-group code
 below and are added to the kernels' results; so do all host matrices.
 
+decompress(r0, r1) produces a dense row window (reference: ColGroup*.decompressToBlock(target,
+rl, ru)): the packed groups in one launch, the others per group on the window's rows.  Right
+indexing decompresses only its rows, and t(X) %*% X is the sum over such windows of the dense
+tsmm (reference: CompressedMatrixBlock.transposeSelfMatrixMultOperations), so neither holds
+the dense matrix.
+
 Planning (cocode): per-column distinct counts on a sample, columns with few distinct values
 are greedily merged while the joint tuple count stays <= 255 (uint8 codes).
 """
@@ -116,9 +122,13 @@ class CLAPack:
     col_*   per packed column (C): its matrix column, the offset of its first value in dvals,
             the value stride (column count), and its group's first tuple / tuple count -- the
             transposed dictionary product is one launch over the columns.
+    mc_*    per matrix column (D): its group's column in codes (-1 for a column outside the packed
+            groups), the offset of its first value in dvals and the value stride -- a row window
+            is decompressed by one launch over the window's cells.
     valid   every code is below its group's tuple count (checked once, here)."""
     __slots__ = ("codes", "toff", "toff_host", "G", "Gp", "T", "index", "dvals", "tup_off", "tup_nc", "tup_c0",
-                 "colidx", "col_out", "col_doff", "col_nc", "col_t0", "col_T", "C", "valid", "_chunks")
+                 "colidx", "col_out", "col_doff", "col_nc", "col_t0", "col_T", "C", "mc_grp", "mc_doff", "mc_nc",
+                 "valid", "_chunks")
 
     def with_dicts(self, groups):
         """The pack of a matrix with the same codes and other dictionary values (scale)."""
@@ -183,6 +193,13 @@ def _build_pack(cm):
     p.col_doff = torch.tensor(doff, **i32)[cgrp] + (torch.arange(p.C, **i32) - torch.tensor(coff, **i32)[cgrp])
     p.col_t0 = p.toff[:G][cgrp]
     p.col_T = torch.tensor(Ts, **i32)[cgrp]
+    at = p.colidx.long()
+    p.mc_grp = torch.full((cm.shape[1],), -1, **i32)
+    p.mc_grp[at] = cgrp.to(torch.int32)
+    p.mc_doff = torch.zeros(cm.shape[1], **i32)
+    p.mc_doff[at] = p.col_doff
+    p.mc_nc = torch.zeros(cm.shape[1], **i32)
+    p.mc_nc[at] = p.col_nc
     return p
 
 
@@ -245,19 +262,101 @@ class CompressedMatrix:
                 f"ratio {self.ratio():.1f})")
 
     # ------------------------------------------------------------------ decompress
-    def decompress(self):
-        out = torch.zeros(self.shape, dtype=self.dtype, device=self.device)
-        for g in self.groups:
+    def decompress(self, r0=0, r1=None):
+        """The dense matrix, or with a range its rows [r0, r1) only (reference:
+        ColGroup*.decompressToBlock(target, rl, ru)): the packed groups of a matrix in HBM in one
+        launch of ops/hip/cla.hip, the other groups -- and every group of a host matrix -- by
+        the per-group code on the window's rows.  An isolated window costs O(window) for UNC and
+        DDC groups and O(stored entries) for OLE / RLE groups."""
+        n = self.shape[0]
+        r0, r1 = int(r0), n if r1 is None else int(r1)
+        if not 0 <= r0 <= r1 <= n:
+            raise ValueError(f"row window [{r0}, {r1}) outside the {n} rows of the matrix")
+        out = torch.empty((r1 - r0, self.shape[1]), dtype=self.dtype, device=self.device)
+        self._window(out, r0, r1)
+        return out
+
+    def _window(self, out, r0, r1, ordered=None):
+        """Fill out ((r1 - r0) x D, any row pitch) with the rows [r0, r1); every cell is written.
+        `ordered`: the OLE / RLE entries by row (_row_ordered) with r0 and r1 among their cuts.
+        True when the packed groups were written by the HIP kernel."""
+        if r1 <= r0:
+            return False
+        groups, hip = self.groups, False
+        p = self._cla(1)
+        if p is not None:
+            from . import kernels
+            if kernels.cla_decompress(p, r0, r1, out) is not None:
+                groups, hip = self._rest(p), True
+        if not hip:
+            out.zero_()
+        for g in groups:
             if g.kind == "unc":
-                out[:, g.cols] = g.dict
+                out[:, g.cols] = g.dict[r0:r1]
             elif g.kind == "ddc":
-                out[:, g.cols] = g.dict.index_select(0, g.codes.long())
+                out[:, g.cols] = g.dict.index_select(0, g.codes[r0:r1].long())
             else:
-                rows, tid = g.entries()
-                blk = torch.zeros((self.shape[0], g.cols.numel()), dtype=self.dtype, device=self.device)
+                if ordered is not None:
+                    rows, tid, cuts = ordered[id(g)]
+                    lo, hi = cuts[r0], cuts[r1]
+                    rows, tid = rows[lo:hi] - r0, tid[lo:hi]
+                else:
+                    rows, tid = g.entries()
+                    if r0 > 0 or r1 < self.shape[0]:
+                        m = (rows >= r0) & (rows < r1)
+                        rows, tid = rows[m] - r0, tid[m]
+                blk = torch.zeros((r1 - r0, g.cols.numel()), dtype=self.dtype, device=self.device)
                 blk[rows] = g.dict.index_select(0, tid)
                 out[:, g.cols] = blk
-        return out
+        return hip
+
+    def _row_ordered(self, bounds):
+        """The stored entries of every OLE / RLE group ordered by row, and for each row in
+        `bounds` the number of entries before it: expanded and sorted once for all the windows
+        between consecutive bounds."""
+        at = torch.tensor(bounds, device=self.device)
+        res = {}
+        for g in self.groups:
+            if g.kind in ("ole", "rle"):
+                rows, tid = g.entries()
+                order = torch.argsort(rows)
+                rows, tid = rows[order], tid[order]
+                res[id(g)] = (rows, tid, dict(zip(bounds, torch.searchsorted(rows, at).tolist())))
+        return res
+
+    # ------------------------------------------------------------------ t(X) %*% X
+    def tsmm(self):
+        """t(X) %*% X without the dense matrix (reference: CompressedMatrixBlock.
+        transposeSelfMatrixMultOperations): the sum, in row order, of the dense tsmm of row
+        windows decompressed into one reused buffer of kernels._CLA_TSMM_SCRATCH bytes.  In HBM
+        the window is written by ops/hip/cla.hip (packed groups) and multiplied by the exact
+        fp32 / fp64 MFMA tsmm of ops/hip/gemm.hip; on the host by addmm."""
+        from . import kernels
+        from .backend import backend
+        n, D = self.shape
+        if n == 0 or D == 0:
+            return torch.zeros((D, D), dtype=self.dtype, device=self.device)
+        es = torch.empty((), dtype=self.dtype).element_size()
+        step = max(1, min(n, kernels._CLA_TSMM_SCRATCH // (D * es)))
+        bounds = list(range(0, n, step)) + [n]
+        mfma = torch.device(self.device).type == "cuda" and backend.use_kernels and \
+            self.dtype in (torch.float32, torch.float64)
+        S = None if mfma else torch.zeros((D, D), dtype=self.dtype, device=self.device)
+        ordered = self._row_ordered(bounds) if len(bounds) > 2 else None
+        buf = torch.empty((step, D), dtype=self.dtype, device=self.device)
+        hip = False
+        for r0, r1 in zip(bounds, bounds[1:]):
+            w = buf[:r1 - r0]
+            hip = self._window(w, r0, r1, ordered) or hip
+            if mfma:
+                from . import gemm
+                Sb = gemm.tsmm(w)
+                S = Sb if S is None else S.add_(Sb)
+            else:
+                S.addmm_(w.t(), w)
+        if hip:
+            kernels._count("cla.tsmm")
+        return S
 
     # ------------------------------------------------------------------ products
     def matmul(self, V):

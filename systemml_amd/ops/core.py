@@ -745,7 +745,14 @@ def tsmm(x, left=True):
     if is_dist(x):
         return _dist().tsmm(x, left)
     if CMP.is_compressed(x):
-        x = x.decompress()
+        if left:
+            # row blocks decompressed into one reused window, never the dense matrix
+            r = x.tsmm()
+            if backend.use_kernels and r.is_cuda:
+                from . import kernels
+                return kernels._result(r)
+            return r
+        x = x.decompress()                  # X %*% t(X): the n x n result dwarfs the dense X
     x = _need_mat(x, "tsmm")
     if SP.is_sparse(x):
         return SP.tsmm(x, left)
@@ -916,6 +923,14 @@ def rix(x, rl, ru, cl, cu, list_mode=False):
         c0, c1 = _bound(cl, 1), _bound(cu, nc)
         _check_range(r0, r1, c0, c1, nr, nc)
         return x.slice(r0 - 1, r1, c0 - 1, c1)
+    if CMP.is_compressed(x):
+        # only the window's rows are decompressed (X[beg:end, ] of a mini-batch loop)
+        nr, nc = x.shape
+        r0, r1 = _bound(rl, 1), _bound(ru, nr)
+        c0, c1 = _bound(cl, 1), _bound(cu, nc)
+        _check_range(r0, r1, c0, c1, nr, nc)
+        out = x.decompress(r0 - 1, r1)
+        return out if (c0, c1) == (1, nc) else out[:, c0 - 1:c1]
     if not isinstance(x, Tensor):
         if getattr(x, "is_part_view", False):           # parfor data partition (runtime/parfor.py)
             return x.part_rix(rl, ru, cl, cu)

@@ -13,6 +13,8 @@
 //   lmm      bins[toff[g] + codes[i, g], :] += Y[i, :]        fp64 LDS bins, per-block slab
 //   dicttmm  out[cols_g[j], :] = sum_t D_g[t, j] * bins[t, :]
 //   chain    t(X) %*% f(X %*% v), K = 1, one pass: gather, f, scatter
+//   decomp   out[i - r0, d] = D_g[codes[i, g], j] for rows r0 <= i < r1 (a dense row window;
+//            reference: ColGroupDDC1.decompressToBlock(target, rl, ru)), lanes along the row
 //
 // Thread mapping: a row is served by a team of L lanes (L = the power of two >= its vector
 // count, at most 64), lane j taking vectors j, j + L, ...: a wave's loads are contiguous 16-byte
@@ -297,6 +299,77 @@ __global__ void __launch_bounds__(NB) chain_kernel(const uint8_t* __restrict__ c
   for (int e = threadIdx.x; e < Tn; e += NB) dst[e] = bins[e];
 }
 
+// Row-window decompression: out[(i - r0) * ldo + d] = the dictionary value of column d in row i,
+// or zero for a column outside the packed groups (mc_grp[d] < 0), for r0 <= i < r1 and d < D.
+// A workgroup takes tiles of R consecutive rows: their code vectors are one contiguous piece of
+// the code matrix, copied to LDS with 16-byte loads.  Then a team of LR lanes walks along an
+// output row, lane j writing the columns [c * W, c * W + W) of chunks c = j, j + LR, ... (W = one
+// 16-byte store when VEC, else one value), so a wave's stores are contiguous; the chunk's column
+// tables are read once per tile and chunk, not per row.  LDSD: the flattened dictionaries are
+// staged in LDS, else read through the cache.  Tiles are independent: no atomics, no order.
+template <typename T, bool VEC, bool LDSD>
+__global__ void __launch_bounds__(NT) decomp_kernel(const uint8_t* __restrict__ codes, int Gp, int64_t r0, int64_t r1,
+                                                    int D, const int* __restrict__ mc_grp,
+                                                    const int* __restrict__ mc_doff, const int* __restrict__ mc_nc,
+                                                    const T* __restrict__ dvals, int ndv, T* __restrict__ out,
+                                                    int64_t ldo, int R, int LR) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  constexpr int W = VEC ? (int)(16 / sizeof(T)) : 1;
+  typedef T Pack __attribute__((ext_vector_type(W)));   // W = 4 / 2: one 16-byte store
+  uint8_t* s_codes = smem;                           // R * Gp bytes, a multiple of 16
+  T* s_dv = (T*)(smem + (size_t)R * Gp);
+  if (LDSD)
+    for (int e = threadIdx.x; e < ndv; e += NT) s_dv[e] = dvals[e];
+  const T* dv = LDSD ? s_dv : dvals;
+  const int V = Gp >> 4, CH = (D + W - 1) / W;
+  const int teams = NT / LR, team = threadIdx.x / LR, j = threadIdx.x % LR;
+  const int64_t ntiles = (r1 - r0 + R - 1) / R;
+  for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const int64_t row0 = r0 + t * R;
+    const int rows = (int)(r1 - row0 < R ? r1 - row0 : R);
+    __syncthreads();                                 // the previous tile's codes are no longer read
+    const uint4* src = (const uint4*)(codes + row0 * Gp);
+    for (int e = threadIdx.x; e < rows * V; e += NT) ((uint4*)s_codes)[e] = src[e];
+    __syncthreads();
+    for (int c = j; c < CH; c += LR) {
+      // a column outside the packed groups reads group 0's code and dvals[0], and writes zero
+      int grp[W], off[W], nc[W];
+      bool on[W];
+#pragma unroll
+      for (int w = 0; w < W; ++w) {
+        const int d = c * W + w;
+        const int g = d < D ? mc_grp[d] : -1;
+        on[w] = g >= 0;
+        grp[w] = on[w] ? g : 0;
+        off[w] = on[w] ? mc_doff[d] : 0;
+        nc[w] = on[w] ? mc_nc[d] : 0;
+      }
+      for (int r = team; r < rows; r += teams) {
+        Pack p;
+#pragma unroll
+        for (int w = 0; w < W; ++w) {
+          const T x = dv[off[w] + (int)s_codes[r * Gp + grp[w]] * nc[w]];
+          p[w] = on[w] ? x : (T)0;
+        }
+        T* dst = out + (row0 - r0 + r) * ldo + (int64_t)c * W;
+        if (c * W + W <= D) {
+          *(Pack*)dst = p;
+        } else {
+#pragma unroll
+          for (int w = 0; w < W; ++w)
+            if (c * W + w < D) dst[w] = p[w];
+        }
+      }
+    }
+  }
+}
+
+// rows of a decompression tile: 16 KiB of codes, at most 256 rows
+int decomp_tile_rows(int Gp) {
+  const int R = 16384 / Gp;
+  return R < 1 ? 1 : R > 256 ? 256 : R;
+}
+
 // rows per block: an even share, rounded up to whole iterations of the block's teams
 int64_t rows_per_block(int64_t n, int grid, int L, int nt = NT) {
   const int64_t span = (int64_t)(nt / L) * UNR;
@@ -389,6 +462,38 @@ int chain_launch(const uint8_t* codes, int64_t n, int Gp, const int* toff, const
   const int64_t rpb = rows_per_block(n, grid, team_lanes(Gp >> 4), NB);
   hipLaunchKernelGGL(fn, dim3(grid), dim3(NB), lds, st, codes, n, Gp, team_lanes(Gp >> 4), toff, P, Tn, u0, w, epi,
                      gout, slab, rpb);
+  return (int)hipGetLastError();
+}
+
+template <typename T>
+int decomp_launch(const uint8_t* codes, int Gp, int64_t r0, int64_t r1, int D, const int* mc_grp, const int* mc_doff,
+                  const int* mc_nc, const T* dvals, int ndv, T* out, int64_t ldo, int grid, hipStream_t st) {
+  const int R = decomp_tile_rows(Gp);
+  const size_t cb = (size_t)R * Gp, db = (size_t)ndv * sizeof(T);
+  const bool in_lds = db <= (size_t)g_budget && cb + db <= kMaxLds;
+  const size_t lds = cb + (in_lds ? db : 0);
+  const bool vec = (ldo * sizeof(T)) % 16 == 0 && (uintptr_t)out % 16 == 0;
+  const int W = vec ? (int)(16 / sizeof(T)) : 1, CH = (D + W - 1) / W;
+  int LR = 1;
+  while (LR < CH && LR < NT) LR <<= 1;
+  const int64_t ntiles = (r1 - r0 + R - 1) / R;
+  if (grid > ntiles) grid = (int)ntiles;
+#define DECOMP(VEC_, LDS_)                                                                                         \
+  do {                                                                                                             \
+    auto fn = decomp_kernel<T, VEC_, LDS_>;                                                                        \
+    if (int rc = allow_lds(fn, lds)) return rc;                                                                    \
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(NT), lds, st, codes, Gp, r0, r1, D, mc_grp, mc_doff, mc_nc, dvals, ndv, \
+                       out, ldo, R, LR);                                                                           \
+  } while (0)
+  if (vec && in_lds)
+    DECOMP(true, true);
+  else if (vec)
+    DECOMP(true, false);
+  else if (in_lds)
+    DECOMP(false, true);
+  else
+    DECOMP(false, false);
+#undef DECOMP
   return (int)hipGetLastError();
 }
 
@@ -487,6 +592,24 @@ int sysml_cla_chain(int dt, const void* codes, int64_t n, int Gp, const int* tof
   if (dt == 2)
     return chain_launch<double>((const uint8_t*)codes, n, Gp, toff, (const double*)P, Tn, (const double*)u0,
                                 (const double*)w, epi, (double*)gout, slab, grid, st);
+  return -1;
+}
+
+// out ((r1 - r0) x D, leading dimension ldo >= D) = rows [r0, r1) of the packed groups, zero in
+// the columns of the other groups (mc_grp < 0); n rows of codes, ndv values in dvals.  16-byte
+// stores when ldo and out allow them.  grid: workgroups at most (one tile of rows each at least)
+int sysml_cla_decompress(int dt, const void* codes, int64_t n, int Gp, int64_t r0, int64_t r1, int D,
+                         const int* mc_grp, const int* mc_doff, const int* mc_nc, const void* dvals, int ndv,
+                         void* out, int64_t ldo, int grid, void* stream) {
+  if (Gp <= 0 || (Gp & 15) || Gp > 16384 || r0 < 0 || r0 >= r1 || r1 > n || D < 1 || ldo < D || ndv < 1 || grid <= 0)
+    return -1;
+  hipStream_t st = (hipStream_t)stream;
+  if (dt == 1)
+    return decomp_launch<float>((const uint8_t*)codes, Gp, r0, r1, D, mc_grp, mc_doff, mc_nc, (const float*)dvals, ndv,
+                                (float*)out, ldo, grid, st);
+  if (dt == 2)
+    return decomp_launch<double>((const uint8_t*)codes, Gp, r0, r1, D, mc_grp, mc_doff, mc_nc, (const double*)dvals,
+                                 ndv, (double*)out, ldo, grid, st);
   return -1;
 }
 

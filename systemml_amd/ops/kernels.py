@@ -238,6 +238,8 @@ def load(required=False):
     L.sysml_cla_lmm.argtypes = [CI, VP, I64, CI, VP, CI, VP, CI, CI, CI, CI, I64, VP, CI, VP]
     L.sysml_cla_chain.restype = CI
     L.sysml_cla_chain.argtypes = [CI, VP, I64, CI, VP, VP, CI, VP, VP, CI, VP, VP, CI, VP]
+    L.sysml_cla_decompress.restype = CI
+    L.sysml_cla_decompress.argtypes = [CI, VP, I64, CI, I64, I64, CI, VP, VP, VP, VP, CI, VP, I64, CI, VP]
     _lib = L
     return L
 
@@ -2186,3 +2188,39 @@ def cla_chain(p, ctype, v, w, u0, out, want_g=False):
     _cla_fold(L, p, slab, 1, 1, out)
     _count("cla.chain")
     return g if want_g else True
+
+
+# Bytes of the dense row window that CompressedMatrix.tsmm decompresses and multiplies per block
+# (ops/compress.py): the window is written by the decompression kernel and read by the tsmm that
+# follows it, so it should still be in the 256 MiB Infinity Cache then -- together with the codes
+# read and the split-K slab written in between; 128 MiB was the starting point by that reasoning.
+# Sweep on an MI355X (tools/bench_cla.py --tsmm, 4M x 256 fp32, profiles/cla_tsmm_kbench.txt):
+#     scratch MiB      32     64    128    256    512   one block (3906)
+#     ms            13.34   8.69   6.58   5.58   4.92   4.27      parent 44.7, dense tsmm alone 3.43
+#     peak MiB         75    107    171    299    555   3949
+# The time is about 4.2 ms + 77 us per block with no knee at the cache size: the blocks' launches
+# and the shorter split-K cost more than a window that leaves the cache.  128 MiB stays: 6.8x
+# faster than the parent at 1 / 23 of its memory; each doubling buys less than it allocates.
+_CLA_TSMM_SCRATCH = 128 << 20
+_CLA_DECOMP_TILE = 16 * 1024     # bytes of codes a workgroup of decomp_kernel holds in LDS
+
+
+def cla_decompress(p, r0, r1, out):
+    """out ((r1 - r0) x D, unit column stride, any row pitch >= D) = rows [r0, r1) of the packed
+    uint8 DDC groups, zero in the columns of the other groups: one launch, every cell of the
+    window written.  None (out untouched) when not applicable."""
+    if not _cla_ok(p, out) or out.dtype != p.dvals.dtype:
+        return None
+    n, D = p.codes.shape[0], p.mc_grp.numel()
+    if not 0 <= r0 < r1 <= n or tuple(out.shape) != (r1 - r0, D) or out.stride(1) != 1 or out.stride(0) < D:
+        return None
+    L = load(required=True)
+    tab = p.dvals.numel() * p.dvals.element_size()
+    lds = _CLA_DECOMP_TILE + (tab if tab <= L.sysml_cla_budget() and _CLA_DECOMP_TILE + tab <= _CLA_LDS_MAX else 0)
+    rc = L.sysml_cla_decompress(_cla_dt(out.dtype), p.codes.data_ptr(), n, p.Gp, r0, r1, D, p.mc_grp.data_ptr(),
+                                p.mc_doff.data_ptr(), p.mc_nc.data_ptr(), p.dvals.data_ptr(), p.dvals.numel(),
+                                out.data_ptr(), out.stride(0), _cla_grid(p, r1 - r0, lds) * 4, _stream())
+    if rc != 0:
+        raise RuntimeError(f"sysml_cla_decompress failed: {rc}")
+    _count("cla.decompress")
+    return out

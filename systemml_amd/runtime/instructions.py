@@ -25,6 +25,8 @@ _SPARSE_OK_OPS = {"lit", "tread", "fout", "fcall", "mm", "tsmm", "mmchain", "t",
 _SPARSE_OK_BI = {"_nnz", "_minus_nz", "_log_nz"}
 # operators computing directly on cbind(X, const) views (ops/augmented.ConstCol)
 _CC_OK_OPS = {"b", "u", "agg", "mm", "tsmm", "mmchain", "smgrad", "smobj", "rix", "t", "cell", "magg", "row"}
+# operators of _CC_OK_OPS that take a compressed matrix (ops/compress.py) as it is
+_CLA_OK_OPS = {"rix"}
 _SPARSE_OK_UNARY = {"nrow", "ncol", "length", "cast_matrix", "abs", "sqrt", "round", "floor", "ceil", "sign",
                     "sin", "tan", "asin", "atan", "sinh", "tanh", "neg"}       # ops/sparse.py SAFE_UNARY
 # operators that accept HBM-resident scalars (runtime/scalars.DevScalar) as operands; all others
@@ -52,9 +54,12 @@ def make_impl(h):
     if sparse_ok and lazy_ok:
         return fn, code
     if h.op in _CC_OK_OPS:
-        # constant-column views (ops/augmented.py) are handled by these operators themselves
-        def is_sp(x, _s=SP.is_special):
-            return _s(x) and type(x).__name__ != "ConstCol"
+        # constant-column views (ops/augmented.py) are handled by these operators themselves,
+        # and so is a compressed operand of right indexing (only the window is decompressed)
+        keep = ("ConstCol", "CompressedMatrix") if h.op in _CLA_OK_OPS else ("ConstCol",)
+
+        def is_sp(x, _s=SP.is_special, _keep=keep):
+            return _s(x) and type(x).__name__ not in _keep
     else:
         is_sp = SP.is_special
     dense = SP.densify
